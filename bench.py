@@ -2,7 +2,7 @@
 """bench.py -- reads/s of the HIP caller on BASELINE.json's workloads.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload headline|cfg1|cfg5]
-                    [--reads R] [--samples T]
+                    [--reads R] [--samples T] [--dump-outputs DIR] [--full]
 
 Workloads (config.workload)
   headline  BASELINE.json configs[2]: 100k synthetic reads, 2 kSample squiggles, HD-style interrupted automaton
@@ -14,8 +14,12 @@ Workloads (config.workload)
   cfg5      BASELINE.json configs[4] at one GPU's share: 8 loci x 2 strands, ~128-state automata, T in [500, 5000],
             50k reads per GPU.
 A "step" is one full call of the batch: both DTW passes, rescaling fit, bad-repeat masking, allele lengths.
-Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.  The results of the timed
-steps are compared with the CPU oracle on a sample of the reads ("verified"); a mismatch exits non-zero.
+Inputs are resident in HBM before the timed region and are the same from run to run (seeded).  One JSON line is printed by
+rank 0.  A plain run sets up, warms up, times K steps and prints the line (ms_per_step: one timed step).
+--dump-outputs DIR: the result records of the last timed step, one float64 array per field, as DIR/<field>.npy.
+--full: everything else the line can carry -- the results of the timed steps compared with the CPU oracle on a sample of
+the reads ("verified"; a mismatch exits non-zero), the CPU baseline, the fill kernel alone and its counters (valu_roofline,
+roofline.traffic), the proof of the ranks, and on the default one-GPU headline run the secondary workloads and driver legs.
 """
 import argparse
 import json
@@ -192,6 +196,30 @@ def verify(gpu_records, oracle_results):
             bad.append(i)
     return {'reads': len(oracle_results), 'mismatches': len(bad), 'first_mismatches': bad[:5],
             'fields': 'status, len1, len2 identical; cost1, cost2 within 1e-5 relative', 'against': 'oracle/ (CPU)'}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the result records a caller of the timed path receives, one float64 array per field as
+    out_dir/<field>.npy (the reserved field left out).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the reads is
+    written instead, with their positions in the workload as index.npy."""
+    fields = [f for f in records.dtype.names if f != 'reserved']
+    cap = DUMP_LIMIT_BYTES // (8 * (len(fields) + 1))
+    if len(records) > cap:
+        idx = np.sort(np.random.default_rng(0).choice(len(records), size=cap, replace=False))
+        records = records[idx]
+    else:
+        idx = None
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(out_dir, f'{f}.npy'), records[f].astype(np.float64))
+    index = os.path.join(out_dir, 'index.npy')
+    if idx is not None:
+        np.save(index, idx.astype(np.float64))
+    elif os.path.exists(index):   # (left by an earlier run into the same directory)
+        os.remove(index)
 
 
 def union_ms(begin, end):
@@ -1025,23 +1053,30 @@ def main():
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak')
     ap.add_argument('--reads', type=int, default=0, help='reads per GPU (weak) / in total (strong); default by workload')
     ap.add_argument('--samples', type=int, default=2000, help='samples per read (headline workload)')
-    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the 15 s CPU baseline (a 256-read check remains)')
-    ap.add_argument('--no-verify', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps: the oracle check, the CPU baseline, the fill kernel alone, the proof of the ranks '
+                         'and (default one-GPU headline run) the secondary workloads and driver legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the result records of the last timed step to DIR/<field>.npy (float64; a fixed sample above 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the 15 s CPU baseline (a 256-read check remains)')
+    ap.add_argument('--no-verify', action='store_true', help='--full: skip the oracle check')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='the default single-GPU headline run also times cfg1, cfg5 and the path from raw int16 segments '
+                    help='the --full single-GPU headline run also times cfg1, cfg5 and the path from raw int16 segments '
                          '(reported under "secondary"); this switch leaves them out')
     ap.add_argument('--workspace-limit-gib', type=float, default=0.0,
                     help='wsx_caller_set_workspace_limit for the main handle (default: the library chooses from the free device memory)')
-    ap.add_argument('--from-fast5', type=int, default=1500, help='copies of the upstream test fast5 in the from_fast5 leg of the default run (0: leave it out)')
-    ap.add_argument('--cfg5-full', type=int, default=50000, help='reads per locus of the cfg5_full leg of the default run: configs[4] at its full '
+    ap.add_argument('--from-fast5', type=int, default=1500, help='copies of the upstream test fast5 in the from_fast5 leg of the --full run (0: leave it out)')
+    ap.add_argument('--cfg5-full', type=int, default=50000, help='reads per locus of the cfg5_full leg of the --full run: configs[4] at its full '
                                                                'size, 8 loci x that many reads, on the one GPU (0: leave it out)')
-    ap.add_argument('--many-loci', type=int, default=2000, help='loci of the many_loci leg of the default run (0: leave it out)')
+    ap.add_argument('--many-loci', type=int, default=2000, help='loci of the many_loci leg of the --full run (0: leave it out)')
     ap.add_argument('--from-raw', action='store_true',
                     help='also time the path from raw int16 segments (host and HBM resident): loader kernels + caller with the '
                          'called sequences requested; reported as from_raw next to the headline')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be at least 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be at least 1 and --warmup at least 0')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # not under a launcher: this process becomes the launcher (before torch or HIP is loaded) and the ranks its children
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1171,18 +1206,23 @@ def main():
     hip.timing_window(False)
     workspace = hip.workspace()  # what the timed steps needed (the single-stream step below is one 100k-read chunk: bigger)
     workspace['limit_bytes'] = hip.workspace_limit()
-    # untimed extra step on ONE stream: the fill kernel's duration when nothing runs beside it (VALU roofline)
-    hip.set_streams(1)
-    step()
-    hip.synchronize()
-    torch.cuda.synchronize()
-    ab, ae, _ = hip.fill_intervals()
-    hip.set_streams(4)
+    # the records of the last timed step, every rank's, as the step delivered them (read before anything else runs)
+    table = allres.cpu().numpy().view(_lib.RESULT_DTYPE).reshape(world, n_pad) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.concatenate([table[r][:(len(shards[r]) if strong else n)] for r in range(world)]))
+    if args.full:
+        # untimed extra step on ONE stream: the fill kernel's duration when nothing runs beside it (VALU roofline)
+        hip.set_streams(1)
+        step()
+        hip.synchronize()
+        torch.cuda.synchronize()
+        ab, ae, _ = hip.fill_intervals()
+        hip.set_streams(4)
     # what proves the ranks and the collective were real: every rank's device, clock and a checksum of the records it computed in
     # the last timed step, all-gathered as objects; rank 0 compares the checksums with those of the slices the step's own
     # all-gather (RCCL: all_gather_into_tensor on the gather stream) delivered
     ranks = None
-    if world > 1 or self_gather:
+    if args.full and (world > 1 or self_gather):
         import zlib
         props = torch.cuda.get_device_properties(local)
         own_n = len(shards[rank]) if strong else n
@@ -1199,7 +1239,6 @@ def main():
 
     rc = 0
     if rank == 0:
-        table = allres.cpu().numpy().view(_lib.RESULT_DTYPE).reshape(world, n_pad)
         mine = table[0][:n]
         ok_all = int(sum((table[r][:(len(shards[r]) if strong else n)]['status'] == 0).sum() for r in range(world)))
         S = max(t.n_states for t in wl.tables)
@@ -1221,15 +1260,13 @@ def main():
         achieved_union = algo_bytes_total / (fill_union * 1e-3) / 1e9
         kernel = hip.kernel_name(0)
         kernels = sorted({hip.kernel_name(a) for a in range(len(wl.tables))})
-        prof = fill_profile(kernel)
+        prof = fill_profile(kernel) if args.full else None   # (the committed counters are quoted by --full runs)
         stale = prof.get('stale') if prof else None
         if stale:
             prof = None
         traffic = None
         if prof is not None and prof.get('hbm_bytes_per_sample') is not None:  # HBM bytes per launch from the PMC passes, scaled to this launch size
             traffic = prof['hbm_bytes_per_sample'] * samples * 2 * args.steps / launches_total
-        alone_ms = float((ae - ab).sum()) / max(len(ab), 1)
-        alone_rows = samples * 2 / max(len(ab), 1)
         cells_per_s = samples * 2 * args.steps * S / (fill_union * 1e-3)
         if wl.name == 'headline':
             head = f'BASELINE configs[{3 if strong else 2}]: '
@@ -1263,14 +1300,17 @@ def main():
                                  'launches of different chunks overlap on different streams, achieved_over_union divides by the '
                                  'union of their intervals instead. min-plus recurrence: bound by fp64 VALU issue and the LDS '
                                  'pipe, not HBM (see valu_roofline)'},
-            'valu_roofline': (valu_roofline(prof, alone_ms, alone_rows, kernel) if prof is not None else
-                              {'launch_ms_alone': alone_ms, 'counters': stale or 'none (profiling run)'}),
             'valu': {'dp_cells_per_s': cells_per_s},
             # first enqueue to last finish of the timed region on the device clock (HIP events), per step
             'device_ms_per_step': tm['total_ms'] / args.steps,
             # device memory the handle holds for this workload (all work sets of all streams), and per sample of a call
             'workspace': workspace,
         }
+        if args.full:
+            alone_ms = float((ae - ab).sum()) / max(len(ab), 1)
+            alone_rows = samples * 2 / max(len(ab), 1)
+            out['valu_roofline'] = (valu_roofline(prof, alone_ms, alone_rows, kernel) if prof is not None else
+                                    {'launch_ms_alone': alone_ms, 'counters': stale or 'none (profiling run)'})
         if ranks is not None:
             import zlib
             seen = [zlib.crc32(table[r][:ranks[r]['reads']].tobytes()) for r in range(world)]
@@ -1282,7 +1322,7 @@ def main():
             if not out['ranks']['gathered_records_equal_every_ranks_own']:
                 rc = 3
                 print('bench.py: the all-gathered records differ from what the ranks computed', file=sys.stderr)
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             nv = min(n, 4096 if not args.no_cpu_baseline else 256)
             sample = wl.signal[: int(wl.offsets[nv])].cpu().numpy()
             ores, base = oracle_sample(wl, sample, nv, 15.0 if not args.no_cpu_baseline else 2.0)
@@ -1299,7 +1339,7 @@ def main():
                                                        'sample': 'upstream WarpSTR.run through Pool(8) on 2 kSample x 64-state '
                                                                  'reads, development container (BASELINE.md section 2); a constant, '
                                                                  'not measured in this run'}
-        secondary = (world == 1 and wl.name == 'headline' and args.reads == 0 and not args.no_secondary and not args.no_verify
+        secondary = (args.full and world == 1 and wl.name == 'headline' and args.reads == 0 and not args.no_secondary and not args.no_verify
                      and not os.environ.get('WARPSTR_BENCH_PROFILING'))
         if (args.from_raw or secondary) and world == 1:
             out['from_raw'] = from_raw_leg(hip, wl, device, max(3, args.steps // 2), 2)

@@ -125,3 +125,26 @@ def test_launcher_relays_the_line_and_the_exit_code(tmp_path, monkeypatch):
     assert 'banner of some library' in ok.stderr
     bad = subprocess.run([sys.executable, '-c', code, '--fail'], capture_output=True, text=True, timeout=300, env=env)
     assert bad.returncode != 0
+
+
+def test_dump_outputs_writes_every_field_as_float64_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 array per field of the result records (reserved left out); above the size limit a fixed
+    seeded sample of the reads, with their positions as index.npy -- the same sample on every run."""
+    rec = np.zeros(1000, dtype=_lib.RESULT_DTYPE)
+    rec['status'] = np.arange(1000) % 3
+    rec['len1'], rec['len2'] = np.arange(1000), np.arange(1000) * 2
+    rec['cost1'], rec['cost2'] = np.linspace(0.1, 0.9, 1000), np.nan
+    bench.dump_outputs(str(tmp_path / 'all'), rec)
+    names = sorted(p.name for p in (tmp_path / 'all').iterdir())
+    assert names == sorted(f'{f}.npy' for f in rec.dtype.names if f != 'reserved')
+    for f in rec.dtype.names:
+        if f != 'reserved':
+            a = np.load(tmp_path / 'all' / f'{f}.npy')
+            assert a.dtype == np.float64 and np.array_equal(a, rec[f].astype(np.float64), equal_nan=True)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 8 * 10 * 100)   # room for 100 reads of the nine fields and the index
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), rec)
+    idx = np.load(tmp_path / 'a' / 'index.npy')
+    assert len(idx) == 100 and np.array_equal(idx, np.load(tmp_path / 'b' / 'index.npy')) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'len2.npy'), 2 * idx)
+    assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) <= 8 * 10 * 100 + 10 * 128   # (+ the .npy headers)

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def _one_line(out):
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--reads', '9000', '--samples', '900', '--steps', '3',
-                          '--warmup', '1'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--warmup', '1', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     d = _one_line(out)
     assert 'cpu_baseline' in d
     assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['higher_is_better'] is True
@@ -53,7 +54,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 @pytest.mark.parametrize('workload', ['cfg1', 'cfg5'])
 def test_bench_other_workloads_keep_the_contract(workload):
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', workload, '--reads', '1500', '--steps', '2',
-                          '--warmup', '1', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--warmup', '1', '--no-cpu-baseline', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     d = _one_line(out)
     assert d['config']['name'] == workload and d['config']['called_ok'] == 1500
     assert d['verified']['mismatches'] == 0 and d['verified']['reads'] > 0
@@ -64,7 +65,7 @@ def test_bench_from_raw_leg_reports_both_variants_and_checks_them():
     from pinned host memory, as a secondary field of the same one line; the leg compares its records and sequences with the
     float64 path."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--reads', '6000', '--samples', '900', '--steps', '2',
-                          '--warmup', '1', '--no-cpu-baseline', '--from-raw'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--warmup', '1', '--no-cpu-baseline', '--from-raw', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     d = _one_line(out)
     f = d['from_raw']
     assert f['reads_per_s_hbm_int16'] > 0 and f['reads_per_s_host_int16'] > 0
@@ -76,7 +77,7 @@ def test_default_run_carries_the_secondary_workloads():
     """The driver's command (no --reads, one GPU): besides the headline, ONE line also holds driver-timed, oracle-checked
     numbers for the flank-110 shape (cfg1), configs[4]'s share (cfg5) and the path from raw int16 segments, and the
     reference's own Python timing as a constant next to the CPU baseline."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1'], capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--full'], capture_output=True,
                          text=True, timeout=900, cwd=ROOT)
     d = _one_line(out)
     if os.environ.get('WARPSTR_BENCH_PROFILING'):
@@ -112,7 +113,7 @@ def test_bench_two_ranks_as_the_driver_launches_it(scaling):
     reads = 6000 if scaling == 'weak' else 9001  # strong: an odd total, so the shards differ in size
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-           '--reads', str(reads), '--samples', '900', '--scaling', scaling, '--no-cpu-baseline']
+           '--reads', str(reads), '--samples', '900', '--scaling', scaling, '--no-cpu-baseline', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     d = _one_line(out)
     assert d['n_gpus'] == 2 and d['scaling'] == scaling
@@ -143,7 +144,7 @@ def test_bare_gpus_2_starts_its_own_ranks(scaling):
     all-gather delivered equal what every rank computed itself.  Both ranks on the one card, gloo."""
     reads = 5000 if scaling == 'weak' else 7001
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--reads', str(reads),
-                          '--samples', '900', '--scaling', scaling, '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                          '--samples', '900', '--scaling', scaling, '--no-cpu-baseline', '--full'], capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=_bare_env(WARPSTR_BENCH_BACKEND='gloo'))
     d = _one_line(out)
     assert d['n_gpus'] == 2 and d['scaling'] == scaling and d['verified']['mismatches'] == 0
@@ -172,7 +173,7 @@ def test_bench_four_ranks_on_the_one_card():
     env = dict(os.environ, WARPSTR_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--steps', '3', '--warmup', '1',
-           '--reads', '8001', '--samples', '900', '--scaling', 'strong', '--no-cpu-baseline']
+           '--reads', '8001', '--samples', '900', '--scaling', 'strong', '--no-cpu-baseline', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     d = _one_line(out)
     assert d['n_gpus'] == 4 and d['scaling'] == 'strong' and d['config']['reads_total'] == 8001 and d['config']['called_ok'] == 8001
@@ -187,7 +188,7 @@ def test_bench_rccl_collective_path_with_a_one_rank_group(scaling):
     (WARPSTR_BENCH_SELF_GATHER=1)."""
     env = dict(os.environ, WARPSTR_BENCH_SELF_GATHER='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--reads', '7001', '--samples', '900', '--steps', '4',
-                          '--warmup', '1', '--scaling', scaling, '--no-cpu-baseline'], capture_output=True, text=True,
+                          '--warmup', '1', '--scaling', scaling, '--no-cpu-baseline', '--full'], capture_output=True, text=True,
                          timeout=600, cwd=ROOT, env=env)
     d = _one_line(out)
     assert 'nccl' in d['config']['results_gather'] and d['scaling'] == scaling
@@ -195,3 +196,25 @@ def test_bench_rccl_collective_path_with_a_one_rank_group(scaling):
     r = d['ranks']   # the proof fields of the N > 1 line, through RCCL itself
     assert r['world_size'] == 1 and r['backend'] == 'nccl' and r['gathered_records_equal_every_ranks_own'] is True
     assert r['per_rank'][0]['reads'] == 7001 and r['per_rank'][0]['device'] == 0
+
+
+def test_plain_run_times_its_steps_and_dumps_what_the_full_run_checks(tmp_path):
+    """A plain run keeps the headline fields and nothing that needs runs or checks of its own (those are --full's), honours
+    --steps, and --dump-outputs writes the last timed step's records.  The same arguments give the same inputs, so a plain run
+    and a --full run -- whose records the oracle checks -- dump identical arrays."""
+    args = ['--reads', '3000', '--samples', '900', '--steps', '5', '--warmup', '1']
+    plain = _one_line(subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args + ['--dump-outputs', str(tmp_path / 'plain')],
+                                     capture_output=True, text=True, timeout=600, cwd=ROOT))
+    assert plain['steps'] == 5 and plain['warmup'] == 1 and plain['ms_per_step'] > 0
+    assert abs(plain['value'] - 3000 / (plain['ms_per_step'] * 1e-3)) <= 1e-6 * plain['value']
+    for k in ('verified', 'cpu_baseline', 'valu_roofline', 'secondary', 'from_raw', 'ranks'):
+        assert k not in plain, k
+    full = _one_line(subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args + ['--no-cpu-baseline', '--full', '--dump-outputs',
+                                    str(tmp_path / 'full')], capture_output=True, text=True, timeout=600, cwd=ROOT))
+    assert full['verified']['mismatches'] == 0 and full['verified']['reads'] >= 256
+    fields = sorted(p.name for p in (tmp_path / 'plain').iterdir())
+    assert fields == sorted(p.name for p in (tmp_path / 'full').iterdir()) and 'status.npy' in fields and 'cost2.npy' in fields
+    for name in fields:
+        a, b = np.load(tmp_path / 'plain' / name), np.load(tmp_path / 'full' / name)
+        assert a.dtype == np.float64 and a.shape == (3000,) and np.array_equal(a, b, equal_nan=True), name
+    assert int((np.load(tmp_path / 'plain' / 'status.npy') == 0).sum()) == plain['config']['called_ok'] == 3000
